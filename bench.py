@@ -14,13 +14,17 @@ torchrun it uses the ranks it is given.
 
 Output: ONE JSON line on rank 0 (the driver contract), with
   roofline      step kernel only: algorithmic bytes (148 B/px x px x pairs per launch) / HIP-event duration measured inside
-                the library on the launch stream; `traffic` = memory-side bytes of the same kernel from rocprofv3 PMC request
-                counters by size (a counters-only child run of this script; null + reason when rocprofv3 is unavailable)
-  cpu_baseline  the CPU oracle (oracle/, a port of the reference's host path) built -O3 -march=native on this box:
+                the library on the launch stream; with --full, `traffic` = memory-side bytes of the same kernel from rocprofv3 PMC
+                request counters by size (a counters-only child run of this script; null + reason when rocprofv3 is unavailable)
+  cpu_baseline  (--full) the CPU oracle (oracle/, a port of the reference's host path) built -O3 -march=native on this box:
                 median of >= 10 repetitions on all cores (`value`) and on one thread
-  configs       secondary, untimed-by-the-driver measurements of the other BASELINE configs: configs[1] as ONE blocking
-                single-pair call (the reference's per-factor call pattern), configs[4] (1280x960, 64-code) batched, and -- with
-                --window -- configs[3] as a real 64-keyframe / 1024-pair window sharded over the ranks.
+  configs       (--full) secondary, untimed-by-the-driver measurements of the other BASELINE configs: configs[1] as ONE blocking
+                single-pair call (the reference's per-factor call pattern), configs[4] (1280x960, 64-code) batched, and -- also
+                with --window alone -- configs[3] as a real 64-keyframe / 1024-pair window sharded over the ranks.
+
+A plain run (no --full) sets up, ramps the clocks, warms up, times `--steps` steps and prints the line: `value`, `ms_per_step`
+and the step kernel's roofline.  `--dump-outputs DIR` writes what the last timed step computed (rank 0's items and the
+assembled normal equations) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import csv
@@ -53,9 +57,16 @@ def parse():
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--cs", type=int, default=32)
     ap.add_argument("--step-blocks", type=int, default=0, help="workgroups per pair (0 = auto)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the rocprofv3 PMC child run (roofline.traffic = null)")
-    ap.add_argument("--no-configs", action="store_true", help="skip the secondary configs[1] / configs[4] measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline line's steps, also measure everything else the line can carry: the other workloads and evaluation mode, "
+                         "the secondary BASELINE configs, the rocprofv3 PMC traffic child runs, the CPU baseline and the per-block parity check "
+                         "(a plain run does none of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed -- rank 0's items (JtJ, Jtr, residual, inliers) and the assembled normal "
+                         "equations (Hd, Ho, g) -- as DIR/<name>.npy (float32 / float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity check")
+    ap.add_argument("--no-traffic", action="store_true", help="with --full: skip the rocprofv3 PMC child runs (roofline.traffic = null)")
+    ap.add_argument("--no-configs", action="store_true", help="with --full: skip the secondary configs[1] / configs[4] measurements")
     ap.add_argument("--window", action="store_true", help="also measure BASELINE configs[3]: 64 keyframes, 1024 pairs over the ranks")
     ap.add_argument("--schedule", choices=["auto", "static", "dynamic"], default="auto",
                     help="auto: the library's default (DFX_SCHEDULE_AUTO); static / dynamic: force one")
@@ -981,8 +992,26 @@ def run_protocol(a, dist, dev, ctx, step, barrier, P):
     return dict(hist=hist, ramp_steps=ramp_steps, elapsed=elapsed, n_launch=n_launch, kern_ms=kern_ms, kern_min_ms=kern_min, kern_max_ms=kern_max)
 
 
+DUMP_MAX_BYTES = 60_000_000   # --dump-outputs: the .npy files of one run stay below 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy.  Should they exceed DUMP_MAX_BYTES together, each array keeps a fixed, seeded
+    sample of its rows (the same fraction for all) and <name>_rows.npy lists which rows they are."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(v.nbytes + 8 * len(v) for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_MAX_BYTES:
+            rows = np.sort(np.random.default_rng(0x5EED).choice(len(v), max(1, len(v) * DUMP_MAX_BYTES // total), replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            v = v[rows]
+        np.save(os.path.join(path, name + ".npy"), v)
+
+
 def main():
     a = parse()
+    if not a.full:   # a plain run measures the headline figure only; --full adds the rest of the line
+        a.no_cpu_baseline = a.no_traffic = a.no_configs = True
     if a.gpus > 1 and "RANK" not in os.environ and not a.pmc_worker:
         self_spawn(a)
     import torch
@@ -1008,8 +1037,9 @@ def main():
     from deepfactors_amd.dist import NormalEquations, PairGraph, PipelinedReduce
     # Imported HERE, far from any timed loop: the first import of scipy.ndimage starts a thread pool whose start-up keeps the host cores busy for
     # a moment -- imported right in front of the tracker loop of tracker_and_geometric_configs() it made that host-driven loop read 0.97 ms
-    # per frame instead of 0.26 (profiles/r04_bench_scipy_import.txt).
-    import scipy.ndimage  # noqa: F401
+    # per frame instead of 0.26 (profiles/r04_bench_scipy_import.txt).  Only that measurement (--full) needs it.
+    if not a.no_configs:
+        import scipy.ndimage  # noqa: F401
 
     W, H, CS, P = a.width, a.height, a.cs, a.pairs
     ctx = dfx.Context(local)
@@ -1109,8 +1139,14 @@ def main():
     if dist is not None:
         dist.all_reduce(chk)
     if rank == 0:
-        got = float((systems[(step_no[0] - 1) % len(systems)] if pipe is None else pipe.last()).g.double().sum())
+        last = systems[(step_no[0] - 1) % len(systems)] if pipe is None else pipe.last()
+        got = float(last.g.double().sum())
         assert abs(got - float(chk[0])) <= 1e-4 * float(chk[1]) + 1e-6, (got, chk.tolist())
+        if a.dump_outputs:   # before anything below reuses `items`
+            dump_outputs(a.dump_outputs, {"items_JtJ": np.stack([it.JtJ for it in its]), "items_Jtr": np.stack([it.Jtr for it in its]),
+                                          "items_residual": np.array([it.residual for it in its], np.float32),
+                                          "items_inliers": np.array([it.inliers for it in its], np.float64),
+                                          "system_Hd": last.Hd.cpu().numpy(), "system_Ho": last.Ho.cpu().numpy(), "system_g": last.g.cpu().numpy()})
 
     out = None
     mode_ran, dyn_ran = ctx.last_mfma_mode(), ctx.last_schedule_dynamic()
@@ -1199,7 +1235,7 @@ def main():
             del ctx
             torch.cuda.synchronize()
             if a.no_traffic:
-                out["roofline"]["traffic_source"] = "skipped (--no-traffic)"
+                out["roofline"]["traffic_source"] = "skipped (--no-traffic)" if a.full else "not measured (a plain run; --full measures it)"
             else:
                 traffic, detail = pmc_traffic(a)
                 out["roofline"]["traffic"] = traffic

@@ -14,7 +14,7 @@
 // slicing of the item dfx_update_depth + dfx_sfm_step return through the C ABI; error() equals 0.5 x the rescaled dfx_sfm_error; the 1e-6
 // relinearisation rule caches and invalidates; TrackFrame's pose equals a loop over dfx_se3_step with the same host algebra, and the
 // device-resident dfx_track_frame lands within 1e-4 of it.
-// Built by tests/cpp/Makefile where /root/reference exists (the binary travels to the GPU box); run by tests/test_gpu_cpp_shim.py.
+// Built into oracle/_ref/ by oracle/Makefile where the reference tree exists (the binary travels with oracle/_ref/); run by tests/test_gpu_cpp_shim.py.
 #include <hip/hip_runtime.h>
 
 #include <cmath>

@@ -158,13 +158,18 @@ class FakeStream:
         pass
 
 
+def _bench():
+    spec = importlib.util.spec_from_file_location("dfx_bench", os.path.join(ROOT, "bench.py"))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
 def _run_main(argv, out_path):
     """bench.main() with the device layer faked; stdout of the call goes to out_path."""
     import deepfactors_amd
     import torch.distributed as tdist
-    spec = importlib.util.spec_from_file_location("dfx_bench", os.path.join(ROOT, "bench.py"))
-    b = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(b)
+    b = _bench()
     # the single-process measurements that drive the tracker, the geometric factor and the host solver are device code end to end (covered on the
     # GPU by tests/test_gpu_tracker.py, test_gpu_sparse_geometric.py, test_gpu_window.py): here only their place in main()'s control flow
     b.tracker_and_geometric_configs = lambda *a, **k: {"configs0_se3_tracker_3level": {"ms_per_frame": 1.0}, "configs2_sparse_geometric_500pts": {"round_ms": 1.0},
@@ -301,13 +306,13 @@ def test_main_two_ranks_fall_back_together_when_the_communicator_cannot_be_creat
 
 
 def test_main_with_the_secondary_configurations(tmp_path, monkeypatch):
-    """The default command's extra measurements (configs[1] single pair and pyramid, configs[4] on both evaluation modes, the configs[2]
+    """--full's extra measurements (configs[1] single pair and pyramid, configs[4] on both evaluation modes, the configs[2]
     relinearisation round, the headline batch on the bf16 split): every code path of secondary_configs / mode_kernel_us runs and lands in
     the line."""
     monkeypatch.delenv("RANK", raising=False)
     monkeypatch.delenv("WORLD_SIZE", raising=False)
     out = tmp_path / "cfg.txt"
-    _run_main([a for a in ARGS if a != "--no-configs"], str(out))
+    _run_main([a for a in ARGS if a != "--no-configs"] + ["--full"], str(out))
     d = _check_line(out.read_text(), 1)
     c = d["configs"]
     assert set(c) >= {"headline_workload_other_mode", "configs1_single_pair_blocking", "configs1_pyramid3_128pairs", "configs4_1280x960_cs64", "configs2_linearize_16kf_120pairs",
@@ -325,6 +330,43 @@ def test_main_with_the_secondary_configurations(tmp_path, monkeypatch):
     assert c["configs4_1280x960_cs64"]["frac"] > 0 and len(c["configs1_pyramid3_128pairs"]["level_by_level_kernel_us"]) == 3 and c["configs1_pyramid3_128pairs"]["one_launch_kernel_us"] > 0
     for k in ("update_depth_batch_64kf", "se3_step_batch_128pairs", "sfm_error_batch_128pairs"):
         assert c[k]["us"] > 0 and c[k]["frac"] > 0
+
+
+def test_plain_run_times_the_headline_only_and_dumps_the_last_step(tmp_path, monkeypatch):
+    """No --full, no --no-* flags: the line carries the headline figure and nothing measured beside it; --dump-outputs writes the last timed step's
+    items and assembled system (float32 / float64), identical for two runs with the same arguments."""
+    monkeypatch.delenv("RANK", raising=False)
+    monkeypatch.delenv("WORLD_SIZE", raising=False)
+    plain = [a for a in ARGS if not a.startswith("--no-")]
+    dumps = []
+    for k in range(2):
+        dumps.append(tmp_path / f"dump{k}")
+        _run_main(plain + ["--dump-outputs", str(dumps[-1])], str(tmp_path / f"plain{k}.txt"))
+        d = _check_line((tmp_path / f"plain{k}.txt").read_text(), 1)
+        assert "configs" not in d and "cpu_baseline" not in d and "parity_blocks" not in d and "--full" in d["roofline"]["traffic_source"]
+    names = {"items_JtJ": (48, 28 * 29 // 2), "items_Jtr": (48, 28), "items_residual": (48,), "items_inliers": (48,),
+             "system_Hd": (49, 22, 22), "system_Ho": (48, 22, 6), "system_g": (49, 22)}
+    assert sorted(p.name for p in dumps[0].iterdir()) == sorted(n + ".npy" for n in names)
+    got = {n: np.load(dumps[0] / (n + ".npy")) for n in names}
+    for n, shape in names.items():
+        assert got[n].shape == shape and got[n].dtype in (np.float32, np.float64), (n, got[n].shape, got[n].dtype)
+        assert np.array_equal(got[n], np.load(dumps[1] / (n + ".npy"))), n
+    assert np.all(got["items_inliers"] > 0.5 * 64 * 48) and np.all(got["items_residual"] > 0)
+    # the system is the assembly of the dumped items: every Jtr entry lands in exactly one slot of g
+    assert abs(got["system_g"].astype(np.float64).sum() - got["items_Jtr"].astype(np.float64).sum()) <= 1e-4 * np.abs(got["items_Jtr"]).sum()
+
+
+def test_dump_outputs_keeps_a_seeded_sample_above_the_size_limit(tmp_path, monkeypatch):
+    b = _bench()
+    monkeypatch.setattr(b, "DUMP_MAX_BYTES", 4000)
+    a = np.arange(1000 * 2, dtype=np.float32).reshape(1000, 2)
+    for k in range(2):
+        b.dump_outputs(str(tmp_path / f"d{k}"), {"a": a, "b": np.ones(500, np.float64)})
+    files = sorted(p.name for p in (tmp_path / "d0").iterdir())
+    assert files == ["a.npy", "a_rows.npy", "b.npy", "b_rows.npy"]
+    rows, got = np.load(tmp_path / "d0" / "a_rows.npy"), np.load(tmp_path / "d0" / "a.npy")
+    assert rows.dtype == np.float64 and np.array_equal(got, a[rows.astype(np.int64)]) and np.array_equal(rows, np.load(tmp_path / "d1" / "a_rows.npy"))
+    assert sum(np.load(tmp_path / "d0" / f).nbytes for f in files) <= 4000
 
 
 def test_main_forced_modes(tmp_path, monkeypatch):

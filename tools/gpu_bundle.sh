@@ -7,7 +7,7 @@
 # steps (ENV=.. pairs in front of a step's arguments go to its environment, e.g. "smallops:DFX_RW_NX=0:tag=direct"):
 #   suite                    python -m pytest tests -m gpu -q                                   -> pytest_gpu.log
 #   tests:<pytest args>      python -m pytest -m gpu -q <args>  (e.g. tests:tests/test_gpu_rowwalk_nx.py)   -> pytest_<n>.log
-#   bench[:tag=T][:args]     python bench.py <args>                                             -> bench[_T].json
+#   bench[:tag=T][:args]     python bench.py --full <args>                                      -> bench[_T].json
 #   ktrace[:args]            bench.py (short form) under rocprofv3 --kernel-trace --stats        -> bench_under_rocprof.json, kernel_trace_dfx.csv, kernel_stats.csv, launch_gaps.txt
 #   smallops[:tag=T]         tools/small_ops_trace.py (warmed HIP-event timing of the row-walk reductions)   -> small_ops_events[_T].json
 #   smallops_trace[:tag=T]   the same under rocprofv3 --kernel-trace, sliced into its phases     -> small_ops_trace[_T].csv (+ events json)
@@ -16,7 +16,7 @@
 #   rccl1[:args]             bench.py under torch.distributed.run with one rank (RCCL initialised, the exchange on real streams)
 #   gnround                  tests/cpp/gn_round_bench 16 7 ; 64 3 16                             -> gn_round_cpp.txt
 #   latency                  tests/cpp/latency_bench                                             -> latency_cpp.txt
-#   cpp                      tests/cpp/{shim,host,comm,ref_callers}_test                          -> cpp_tests.txt
+#   cpp                      tests/cpp/{shim,host,comm}_test, oracle/_ref/ref_callers_test       -> cpp_tests.txt
 #   tracker                  tools/profile_tracker.py                                            -> tracker.json
 #   pyramid                  tools/pyr_call.sh (pyramid tests, events for 64 frames / 1 frame, kernel-trace timeline) -> pyr/*
 #   pyramid_traffic          tools/pyramid_traffic.sh (TCC_EA0 request counters of the build's launches)    -> pyr_traffic/pyramid_traffic.txt
@@ -46,7 +46,7 @@ for spec in "$@"; do
   case "$step" in
     suite) env "${envs[@]}" timeout 1500 python -m pytest tests -m gpu -q $args > $OUT/pytest_gpu$tag.log 2>&1 < /dev/null; rc=$?; tail -4 $OUT/pytest_gpu$tag.log;;
     tests) env "${envs[@]}" timeout 900 python -m pytest -m gpu -q -x $args > $OUT/pytest_$n$tag.log 2>&1 < /dev/null; rc=$?; tail -6 $OUT/pytest_$n$tag.log;;
-    bench) env "${envs[@]}" timeout 1200 python bench.py $args > $OUT/bench$tag.json 2> $OUT/bench$tag.err < /dev/null; rc=$?
+    bench) env "${envs[@]}" timeout 1200 python bench.py --full $args > $OUT/bench$tag.json 2> $OUT/bench$tag.err < /dev/null; rc=$?
            python - "$OUT/bench$tag.json" <<'PY'
 import json, sys
 try:
@@ -95,7 +95,7 @@ PY
            tail -c 600 $OUT/bench_rccl_1rank$tag.json | cut -c1-600;;
     gnround) { timeout 200 tests/cpp/gn_round_bench 16 7; timeout 300 tests/cpp/gn_round_bench 64 3 16; } > $OUT/gn_round_cpp$tag.txt 2>&1 < /dev/null; rc=$?; cat $OUT/gn_round_cpp$tag.txt;;
     latency) timeout 120 tests/cpp/latency_bench > $OUT/latency_cpp$tag.txt 2>&1 < /dev/null; rc=$?; tail -14 $OUT/latency_cpp$tag.txt;;
-    cpp) rc=0; for t in shim_test host_test host_logic_test comm_test ref_callers_test; do [ -x tests/cpp/$t ] && { e=(); [ $t = comm_test ] && e=(DFX_RCCL_LIB=$PWD/tests/cpp/librccl_stub.so); env "${e[@]}" timeout 300 tests/cpp/$t 2>&1 | tail -2; r=${PIPESTATUS[0]}; [ $r -ne 0 ] && rc=$r; }; done > $OUT/cpp_tests$tag.txt 2>&1 < /dev/null; cat $OUT/cpp_tests$tag.txt;;
+    cpp) rc=0; for t in tests/cpp/shim_test tests/cpp/host_test tests/cpp/host_logic_test tests/cpp/comm_test oracle/_ref/ref_callers_test; do [ -x $t ] && { e=(); [ $t = tests/cpp/comm_test ] && e=(DFX_RCCL_LIB=$PWD/tests/cpp/librccl_stub.so); env "${e[@]}" timeout 300 $t 2>&1 | tail -2; r=${PIPESTATUS[0]}; [ $r -ne 0 ] && rc=$r; }; done > $OUT/cpp_tests$tag.txt 2>&1 < /dev/null; cat $OUT/cpp_tests$tag.txt;;
     pyramid) timeout 600 tools/pyr_call.sh $OUT/pyr > $OUT/pyramid$tag.log 2>&1 < /dev/null; rc=$?; grep -E "build_pyramid|median|passed|failed" $OUT/pyramid$tag.log | cut -c1-150;;
     pyramid_traffic) timeout 400 tools/pyramid_traffic.sh $OUT/pyr_traffic > $OUT/pyramid_traffic$tag.log 2>&1 < /dev/null; rc=$?; tail -4 $OUT/pyramid_traffic$tag.log | cut -c1-200;;
     tracker) timeout 120 python tools/profile_tracker.py > $OUT/tracker$tag.json 2>/dev/null < /dev/null; rc=$?; tail -2 $OUT/tracker$tag.json;;
